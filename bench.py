@@ -10,7 +10,9 @@ per-GPU batch 16, bf16 MFMA compute with fp32 accumulation / residual stream / m
 batch is fixed, ``value`` is the whole-job samples/s.
 
 Rank 0 prints ONE JSON line with the extra ``roofline`` (dominant kernel, live HIP-event timing of every GEMM launch on
-the launch stream during extra instrumented steps) and ``cpu_baseline`` (the CPU oracle timed on the host cores) objects.
+the launch stream during extra instrumented steps) and ``cpu_baseline`` (the CPU oracle timed on the host cores) objects; the
+per-kernel tables and the secondary configurations' details go to ``--details FILE`` only.  ``--dump-outputs DIR`` writes what the
+last timed step returned as ``.npy`` files.
 """
 
 from __future__ import annotations
@@ -196,6 +198,47 @@ def cpu_baseline(kw: dict, state_dict: dict, batch: int, budget_s: float, device
                       f"see `parity` for the like-for-like comparison); {cores} intra-op threads of the host's {host_cores} cores (more threads are slower on this graph)"}, parity
 
 
+DUMP_PARAM_SAMPLE = 1 << 22  # updated weights written by --dump-outputs: 4 Mi fp32 values (16 MB)
+
+
+def dump_outputs(out_dir: str, loss: torch.Tensor, grad_norm: torch.Tensor, metrics: dict, model: torch.nn.Module) -> None:
+    """``--dump-outputs``: what a caller of the timed step received from its last call, as float32 ``<name>.npy`` files - ``loss``, ``grad_norm``, one
+    ``metric_<key>`` per metric tensor, and ``params_sample``, the weights after that step's update: all parameters concatenated in ``named_parameters``
+    order (the reference's state_dict order), or a fixed-seed sample of DUMP_PARAM_SAMPLE of them (sorted positions) when there are more."""
+    import numpy as np
+
+    arrays = {"loss": loss, "grad_norm": grad_norm, **{f"metric_{k}": v for k, v in metrics.items()}}
+    arrays = {k: torch.as_tensor(v).detach().float().cpu().numpy() for k, v in arrays.items()}
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for _, p in model.named_parameters()])
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            pos = torch.randint(0, flat.numel(), (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[pos.to(flat.device)]
+        arrays["params_sample"] = flat.cpu().numpy()
+    path = Path(out_dir)
+    path.mkdir(parents=True, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(path / f"{name}.npy", arr)
+
+
+def result_line(out: dict) -> dict:
+    """The printed result line: ``out`` without the per-kernel tables of ``roofline`` and with ``secondary`` cut to each configuration's step time.  The whole
+    object (over 8 KB at the default workload) no longer fits in what a driver keeps of a run's output; ``--details FILE`` writes all of it."""
+    line = dict(out)
+    if isinstance(line.get("roofline"), dict):
+        line["roofline"] = {k: v for k, v in line["roofline"].items() if k not in ("all_gemm_kernels", "hbm_kernels", "traffic_binding")}
+    if isinstance(line.get("secondary"), dict):
+        line["secondary"] = {k: ({m: v[m] for m in ("ms_per_step", "samples_per_s", "error") if m in v} if isinstance(v, dict) else v)
+                             for k, v in line["secondary"].items()}
+    return line
+
+
+def emit(out: dict, details: str | None) -> None:
+    if details:
+        Path(details).write_text(json.dumps(out) + "\n")
+    print(json.dumps(result_line(out)), flush=True)
+
+
 def _latest_profile(suffix: str) -> str:
     """Newest committed counter capture by round prefix (profiles/rNN_<suffix>; tools/gpu_pmc_round.sh writes them, stamped with the library's sha256)."""
     hits = sorted(p.name for p in (ROOT / "profiles").glob(f"r[0-9][0-9]_{suffix}"))
@@ -317,7 +360,7 @@ def seg_main(args, rank: int, world: int, device: str, sync) -> None:  # noqa: A
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss, gnorm, _ = step(batches[i % 2])
+        loss, gnorm, metrics = step(batches[i % 2])
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -326,6 +369,8 @@ def seg_main(args, rank: int, world: int, device: str, sync) -> None:  # noqa: A
         dt = float(t)
     final_loss = float(loss)
     peak_gib = round(torch.cuda.max_memory_reserved() / 2**30, 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, gnorm, metrics, model)
     n_launches = next(iter(step._recorded.values())).n_launches if step._recorded else None  # noqa: SLF001
     step.replay = False  # the per-launch event timing below goes through the module code
     roofline = None
@@ -372,7 +417,7 @@ def seg_main(args, rank: int, world: int, device: str, sync) -> None:  # noqa: A
                "roofline": roofline}
         if world == 1 and args.cpu_budget > 0:
             out["cpu_baseline"], out["parity"] = seg_cpu_baseline(kw, cpu_state, device, args.cpu_budget)
-        print(json.dumps(out), flush=True)
+        emit(out, args.details)
 
 
 def secondary_configs(device: str, with_parity: bool) -> dict:
@@ -589,7 +634,13 @@ def main() -> None:
                          "reduce_scatter_tensor + all_gather_into_tensor on the flat ranges (one-hop phases on the fully connected xGMI mesh)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short config-4 / config-5 measurements appended to the default one-GPU line")
     ap.add_argument("--no-blas-reference", action="store_true", help="skip the hipBLASLt timing of the step's GEMM shapes (roofline.all_gemm_kernels[*].vs_hipblaslt)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (loss, gradient norm, metrics, a fixed sample of the updated "
+                    "weights) as float32 DIR/<name>.npy; the inputs depend on the arguments only, so two builds can be compared output for output")
+    ap.add_argument("--details", metavar="FILE", help="write the whole result object (per-kernel tables, secondary configurations with their parity) to FILE; "
+                    "the printed line leaves those tables out")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -664,7 +715,7 @@ def main() -> None:
     k0 = K.kernel_launch_count()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss, gnorm, _ = step(batches[i % 2], 0.75)
+        loss, gnorm, metrics = step(batches[i % 2], 0.75)
     barrier()
     dt = time.perf_counter() - t0
     kernels_per_step = round((K.kernel_launch_count() - k0) / max(1, args.steps), 1)  # the library's own count over the timed steps (+ 1 torch fill: zero_grad)
@@ -675,6 +726,8 @@ def main() -> None:
     final_loss = float(loss)
     n_launches = next(iter(step._recorded.values())).n_launches if step._recorded else None  # noqa: SLF001
     peak_gib = round(torch.cuda.max_memory_reserved() / 2**30, 1)  # of 288: parameters + optimiser state + the recorded step's private pool
+    if args.dump_outputs and rank == 0:  # before the information-only steps below overwrite the step's outputs and update the weights again
+        dump_outputs(args.dump_outputs, loss, gnorm, metrics, model)
     # ---- N > 1: how much of the gradient exchange hides behind the backward pass (every rank runs the same extra steps; the replicas diverge
     # in the "no exchange" mode, which is why this comes after the timed region).  exposed = overlapped step - step without exchange;
     # unoverlapped = step with every collective after the backward - step without exchange
@@ -832,7 +885,7 @@ def main() -> None:
                 per_sample = (b64["ms_per_step"] - out["ms_per_step"]) / 48.0
                 out["config"]["fixed_ms_per_step"] = round(out["ms_per_step"] - 16.0 * per_sample, 3)
                 out["config"]["marginal_ms_per_sample"] = round(per_sample, 4)
-        print(json.dumps(out), flush=True)
+        emit(out, args.details)
     if world > 1 or args.force_sync:
         dist.destroy_process_group()
 
