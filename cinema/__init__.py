@@ -2,9 +2,9 @@
 
 ``from cinema import CineMA, ConvViT, ConvUNetR, patchify, unpatchify`` and the sub-module imports the reference's training / inference
 scripts use (``cinema.mae.mae``, ``cinema.convvit``, ``cinema.vit``, ``cinema.conv``, ``cinema.rotary``, ``cinema.optim``, ``cinema.device``, ``cinema.transform``,
-``cinema.segmentation.convunetr``, ``cinema.segmentation.train``, ``cinema.classification.train``, ``cinema.regression.train``) resolve to the ``cinema_amd`` modules of the same name: one set of
-classes, two import names.  Only the hot path is aliased; data loading, hydra entry points, the landmark models and the ResNet / UNet
-baselines are not part of this build and are not faked here.
+``cinema.segmentation.convunetr``, ``cinema.segmentation.train``, ``cinema.classification.train``, ``cinema.regression.train``, ``cinema.segmentation.landmark.train``,
+``cinema.regression.landmark.train``) resolve to the ``cinema_amd`` modules of the same name: one set of classes, two import names.  Only the hot path is
+aliased; data loading, hydra entry points and the ResNet / UNet baselines are not part of this build and are not faked here.
 """
 
 import importlib
@@ -25,11 +25,15 @@ _ALIASES = {
     "cinema.segmentation": "cinema_amd.segmentation",
     "cinema.segmentation.convunetr": "cinema_amd.segmentation.convunetr",
     "cinema.segmentation.train": "cinema_amd.segmentation.train",
+    "cinema.segmentation.landmark": "cinema_amd.segmentation.landmark",
+    "cinema.segmentation.landmark.train": "cinema_amd.segmentation.landmark.train",
     "cinema.train": "cinema_amd.train",
     "cinema.classification": "cinema_amd.classification",
     "cinema.classification.train": "cinema_amd.classification.train",
     "cinema.regression": "cinema_amd.regression",
     "cinema.regression.train": "cinema_amd.regression.train",
+    "cinema.regression.landmark": "cinema_amd.regression.landmark",
+    "cinema.regression.landmark.train": "cinema_amd.regression.landmark.train",
 }
 for _alias, _target in _ALIASES.items():
     _mod = importlib.import_module(_target)

@@ -201,6 +201,12 @@ _PROTOS = {
     "cinema_seg_metric_counts": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "cinema_mask_edges": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
     "cinema_min_dist": [_vp, _vp, _i, _i, _vp, _vp],
+    "cinema_landmark_loss_fwd": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "cinema_landmark_loss_bwd": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "cinema_landmark_window_accumulate": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "cinema_landmark_window_finish": [_vp, _vp, _i, _ll, _vp, _vp],
+    "cinema_heatmap_metrics": [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp],
+    "cinema_head_wing": [_vp, _vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp],
     "cinema_segment_mean_fwd": [_vp, _i, _i, _i, _i, _f, _vp, _vp],
     "cinema_segment_mean_bwd": [_vp, _i, _i, _i, _f, _vp, _i, _i, _vp],
     "cinema_scale_f32": [_vp, _f, _vp, _ll, _vp],
@@ -603,6 +609,7 @@ def info() -> dict:
 # ---- the kernel families (one module per csrc/ source group), re-exported: callers write hip.<name> ----------------------------------------------------
 from cinema_amd.hip.gemm import *  # noqa: E402, F401, F403
 from cinema_amd.hip.loss import *  # noqa: E402, F401, F403
+from cinema_amd.hip.landmark import *  # noqa: E402, F401, F403
 from cinema_amd.hip.rows import *  # noqa: E402, F401, F403
 from cinema_amd.hip.norm import *  # noqa: E402, F401, F403
 from cinema_amd.hip.attention import *  # noqa: E402, F401, F403

@@ -3,7 +3,8 @@
 ``stability_score`` and ``get_volumes`` of device tensors count voxels with ``cinema_seg_metric_counts`` (one pass over the channels-first logits, the same
 kernel :func:`cinema_amd.segmentation.train.segmentation_metrics` uses); the scalar formulas (ejection fraction, its region, coefficient of variance) are
 host arithmetic on whatever the caller passes (floats, numpy arrays, tensors), as in the reference.  ``heatmap_argmax`` / ``heatmap_soft_argmax``
-(exported from the package root, ``cinema/__init__.py:5``) are plain tensor functions - the landmark models themselves are outside this build."""
+(exported from the package root, ``cinema/__init__.py:5``) are plain tensor functions; the landmark evaluation itself computes its soft-argmax coordinates
+in ``cinema_heatmap_metrics`` (:func:`cinema_amd.segmentation.landmark.train.landmark_detection_metrics`)."""
 
 from __future__ import annotations
 

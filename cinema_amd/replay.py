@@ -190,3 +190,55 @@ class RecordedSegStep:
                     raise K.HipLibraryError(f"replayed launch {fn.__name__} failed: {rc}")
         self.loss, self.metrics = self._collect()
         return self.loss, self.metrics
+
+
+class RecordedLandmarkStep(RecordedSegStep):
+    """forward + heatmap loss (sigmoid Dice + BCE) + backward of the landmark-detection fine-tuning step as a launch list: :class:`RecordedSegStep` with the
+    landmark loss kernels, which read the labels as fp32 channels-first heatmaps (the dataset layout, no transpose).  ``run(batch)`` -> (loss, metrics) with
+    the keys of ``landmark_detection_loss``."""
+
+    def __init__(self, model: torch.nn.Module, views: list, batch: dict, audit: bool = False) -> None:  # noqa: D107
+        self.model, self.views = model, list(views)
+        dev = next(model.parameters()).device
+        self.images = {v: batch[f"{v}_image"].detach().to(dev).float().contiguous().clone() for v in self.views}
+        self.labels = {v: batch[f"{v}_label"].detach().to(dev).reshape(-1).float().contiguous().clone() for v in self.views}  # run() copies into these
+        self.batch = next(iter(self.images.values())).shape[0]
+        self.pool = torch.cuda.MemPool()
+        self.unaccounted: list = []
+        T.WEIGHTS.invalidate()
+        calls: list = []
+        K.RECORD = calls
+        try:
+            with torch.cuda.use_mem_pool(self.pool):
+                if audit:
+                    with _Audit(self.unaccounted):
+                        self._eager_step()
+                else:
+                    self._eager_step()
+        finally:
+            K.RECORD, T.REC_CALL = None, None
+        self.calls = calls
+        self.n_launches = sum(1 for fn, _ in calls if fn is not None)
+        self.loss, self.metrics = self._collect()
+
+    def _eager_step(self) -> None:
+        rows = self.model.forward_rows(self.images)
+        up = K.full((1,), 1.0 / len(self.views), torch.float32, self.labels[self.views[0]].device)
+        self.out4, grads = {}, []
+        for v in self.views:
+            out4, coef = K.landmark_loss_fwd(rows[v], self.labels[v], self.batch)
+            grads.append(K.landmark_loss_bwd(rows[v], self.labels[v], self.batch, coef, up))
+            self.out4[v] = out4
+        T.REC_CALL.backward(*grads)
+
+    def _collect(self) -> tuple:
+        with allowed_aten():
+            metrics, n = {}, len(self.views)
+            for v in self.views:
+                o = self.out4[v]
+                metrics.update({f"{v}_bce_loss": o[1], f"{v}_dice_loss": o[2], f"{v}_loss": o[0], f"{v}_{v}_loss": o[0]})
+            loss = sum(self.out4[v][0] for v in self.views) / n
+            metrics["loss"] = loss
+            for k in ("bce_loss", "dice_loss"):
+                metrics[k] = sum(metrics[f"{v}_{k}"] for v in self.views) / n
+            return loss, metrics

@@ -102,9 +102,14 @@ class SegTrainStep(FineTuneStep):
     pass ``weight_decay=0.01`` for torch's default as the reference's from-scratch branch uses it) -> zero_grad.  Returns (loss, grad_norm | None,
     metrics) as device tensors."""
 
+    # the loss on device tensors (eager path) and the cinema_amd.replay class that records / replays the step (replay=True); subclasses for other
+    # heads of the same model swap both
+    loss_tensors = staticmethod(segmentation_loss_tensors)
+    recorded_step = "RecordedSegStep"
+
     def __init__(self, model, views: list, lr: float = 1e-3, betas: tuple = (0.9, 0.95), weight_decay: float = 0.05, layer_decay: float | None = 0.75,  # noqa: ANN001
                  clip_grad: float | None = 5.0, synchronizer=None, replay: bool = False, audit: bool = False, check_every: int = 100) -> None:  # noqa: ANN001
-        super().__init__(model, views, segmentation_loss_tensors, lr=lr, betas=betas, weight_decay=weight_decay, layer_decay=layer_decay,
+        super().__init__(model, views, self.loss_tensors, lr=lr, betas=betas, weight_decay=weight_decay, layer_decay=layer_decay,
                          clip_grad=clip_grad, synchronizer=synchronizer, check_every=check_every)
         # replay: forward + loss + backward recorded once per input signature as the flat list of this library's launches and re-issued from it
         # (cinema_amd/replay.py RecordedSegStep): the module code needs ~50 ms of host time for the ~2000 launches of config 4, as long as the GPU needs
@@ -124,14 +129,14 @@ class SegTrainStep(FineTuneStep):
     def _call(self, batch: dict, n_accum_steps: int, update_grad: bool) -> tuple:
         if not (self.replay and n_accum_steps == 1 and self.model.training):
             return super().__call__(batch, n_accum_steps, update_grad)
-        from cinema_amd.replay import RecordedSegStep
+        from cinema_amd import replay
 
         if self.sync is not None:
             self.sync.arm(update_grad)
         key = tuple((v, tuple(batch[f"{v}_image"].shape), tuple(batch[f"{v}_label"].shape)) for v in self.views)
         rec = self._recorded.get(key)
         if rec is None:  # the recording IS this step
-            rec = self._recorded[key] = RecordedSegStep(self.model, self.views, batch, audit=self.audit)
+            rec = self._recorded[key] = getattr(replay, self.recorded_step)(self.model, self.views, batch, audit=self.audit)
             loss, metrics = rec.loss, rec.metrics
         else:
             loss, metrics = rec.run(batch)

@@ -419,6 +419,37 @@ int cinema_seg_metric_counts(const float* logits, const int* labels, int b, int 
 int cinema_mask_edges(const int* label, int b, int X, int Y, int Z, int c, int ndim, unsigned char* edges, void* stream);
 int cinema_min_dist(const float* a, const float* b_points, int na, int nb, float* out, void* stream);
 
+/* Landmark localisation (csrc/landmark.hip).  Every reduction is formed in a fixed order (per-block partial slabs, no float atomics): the same inputs
+ * give bitwise-equal outputs.
+ *   landmark_loss_fwd / _bwd: heatmap loss of one view (reference _landmark_detection_loss, cinema/segmentation/landmark/train.py:109-132):
+ *       monai DiceLoss(include_background=True) of sigmoid(logits) against soft labels (smooth_nr = smooth_dr = 1e-5, mean over b x c) + BCEWithLogitsLoss
+ *       (mean over b x c x vox).  logits fp32 channels-last rows [b*vox][c] (1 <= c <= 16), labels fp32 channels-first [b][c][vox] (any vox).
+ *       fwd: slab = scratch of at least b * CINEMA_LANDMARK_MAX_BLOCKS * (3c + 1) floats (fully overwritten); out4 = {loss, bce, dice, 0};
+ *       coef [b][c][2] = (d dice / d I, d dice / d P) with I = sum sigmoid(x) t, P = sum sigmoid(x), consumed by bwd.
+ *       bwd: dlogits [b*vox][c] = upstream[0] * ((sigmoid - t) / (b c vox) + sigmoid (1 - sigmoid) (coef_I t + coef_P)) (upstream NULL = 1).
+ *   landmark_window_accumulate / _finish: sliding-window forward of the detection model (reference landmark_detection_forward, train.py:135-208):
+ *       accumulate adds sigmoid(window_logits) (fp32 channels-last rows [px*py*pz][c]) into prob_sum (channels-last [X*Y*Z][c]) at (sx,sy,sz), count += 1
+ *       (both zeroed by the caller; windows are accumulated one launch after the other in grid order); finish writes logits_out [c][X*Y*Z] (channels-first) =
+ *       log(p / (1 - p)) of p = prob_sum / count, unclamped as in the reference: where p rounds to 1 in fp32 the result is +inf.
+ *   heatmap_metrics: per (sample, channel) map (reference landmark_detection_metrics, train.py:257-288, and heatmap_soft_argmax, cinema/metric.py:62-81):
+ *       logits / labels fp32 channels-first [b][c][w*h], element (x, y) at x * h + y; out [b][c][8] = {E[x], E[y] under softmax(beta * sigmoid(logits)),
+ *       E[x], E[y] under softmax(beta * labels), I, P, G, dice loss 1 - (2I + 1e-5) / (G + P + 1e-5)} (the soft-argmax by an online max / sum merge, one pass).
+ *   head_wing: Wing loss of the coordinate-regression head (reference landmark_regression_loss, WingLoss, get_relative_distances,
+ *       cinema/regression/landmark/train.py:46-152): pred / label fp32 [b][n] (normalised), scales fp32 [b][n] (NULL = 1); coordinates = value x scale;
+ *       wing(e) = w log(1 + e / epsilon) for e < w, else e - (w - w log(1 + w / epsilon)).  rel = 1 (n == 6): also the relative distances coords @ M
+ *       (point 1 minus the midpoint of points 2 and 3, ...).  out5 = {loss = landmark wing + rel-dist wing, landmark wing, rel-dist wing, landmark MAE,
+ *       rel-dist MAE} (means over b x n; rel = 0: the rel-dist terms are 0); dpred [b][n] = d loss / d pred (0 where the error is exactly 0). */
+#define CINEMA_LANDMARK_MAX_BLOCKS 64
+int cinema_landmark_loss_fwd(const float* logits, const float* labels, int b, int vox, int c, float* slab, float* out4, float* coef, void* stream);
+int cinema_landmark_loss_bwd(const float* logits, const float* labels, int b, int vox, int c, const float* coef, const float* upstream, float* dlogits,
+                             void* stream);
+int cinema_landmark_window_accumulate(const float* window_logits, int c, int px, int py, int pz, int sx, int sy, int sz, int X, int Y, int Z,
+                                      float* prob_sum, float* count, void* stream);
+int cinema_landmark_window_finish(const float* prob_sum, const float* count, int c, long long n_voxels, float* logits_out, void* stream);
+int cinema_heatmap_metrics(const float* logits, const float* labels, int b, int c, int w, int h, float beta, float* out, void* stream);
+int cinema_head_wing(const float* pred, const float* label, const float* scales, int b, int n, float w, float epsilon, int rel, float* out5, float* dpred,
+                     void* stream);
+
 /* Token pooling of the ConvViT heads (reference cinema/convvit.py:523-547, `x.mean(dim=1, keepdim=True)` and the mean over head outputs):
  * out[s][:] = scale * sum of the seg_rows consecutive rows of segment s of x (fp32 [n_seg*seg_rows][c]); bwd broadcasts scale * dy[s] back. */
 int cinema_segment_mean_fwd(const float* x, int ldx, int n_seg, int seg_rows, int c, float scale, float* out, void* stream);
